@@ -7,6 +7,7 @@
 //     with fp32 global atomics) and generic axpby.
 // All loads/stores are 16-byte vectorised where the layout allows.
 #include <type_traits>
+#include "clip_args.h"
 #include "common.h"
 
 namespace ea {
@@ -488,3 +489,89 @@ extern "C" hipError_t ea_poison_lds(unsigned pattern, hipStream_t s) {
   return hipGetLastError();
 }
 
+// ---- gradient clipping (last in the file: the kernels above keep their code and labels)
+namespace ea {
+
+// the layer whose tiles hold tile t of a replica (find_tile's walk; the clipped update's scale index)
+__device__ __forceinline__ int find_tile_seg(const FlatArgs& a, int t) {
+  int seg = 0, base = 0;
+#pragma unroll
+  for (int q = 0; q < MAX_SEG; ++q) {
+    if (q < a.nseg) {
+      if (t >= base) seg = q;
+      base += ((a.seg[q].K + 63) / 64) * ((a.seg[q].N + 63) / 64);
+    }
+  }
+  return seg;
+}
+
+// The UPDATE tiles of an optimizer with clipvalue / clipnorm / global_clipnorm (per-step path):
+// the optimizer sees g = clamp(G * grad_scale) * scale[r][2 * seg + is_bias], the scales from
+// clip.hip.  A kernel of its own with its parameters in a struct of their own: OptParams and
+// opt_update are shared with every fused epilogue, and shadow_tiles_kernel's instantiations
+// keep their code (a shared inlined body changed their register allocation).
+template <typename T>
+__global__ __launch_bounds__(256) void shadow_tiles_clip_kernel(FlatArgs a, int tiles_per_replica, ClipUpd cu) {
+  __shared__ float tile[64][65];
+  const int r = __builtin_amdgcn_readfirstlane(blockIdx.x % a.R);  // replica-minor, as shadow_tiles_kernel
+  const int t = __builtin_amdgcn_readfirstlane(blockIdx.x / a.R);
+  int lt;
+  const TileV g = find_tile(a, t, lt);
+  const int k0 = (lt / g.tn) * 64, n0 = (lt % g.tn) * 64;
+  const long long iter = a.ctr[2 + r];
+  if ((long long)a.ntrain[r] - a.ctr[0] * a.B <= 0) return;  // replica has no batch this step
+  const int p0 = (int)((iter + 1) & 1);
+  float sc_w = 1.f, sc_b = 1.f;
+  if (cu.scale) {
+    const int seg = find_tile_seg(a, t);
+    sc_w = cu.scale[(long long)r * CLIP_MAX_VAR + 2 * seg];
+    sc_b = cu.scale[(long long)r * CLIP_MAX_VAR + 2 * seg + 1];
+  }
+  const float cv = cu.clipvalue;
+  const float* G = a.G + (long long)r * a.sG;
+  auto grad = [&](long long pi, float sc) {
+    float gv = G[pi] * a.op.grad_scale;
+    if (cv >= 0.f) gv = gv < -cv ? -cv : (gv > cv ? cv : gv);   // NaN passes through
+    return gv * sc;
+  };
+  float* P = a.P + (long long)r * a.sP;
+  float* S = a.S ? a.S + (long long)r * a.sS : nullptr;
+  const int tid = threadIdx.x, nn = tid & 63;
+  T* W = a.Wsh ? reinterpret_cast<T*>(a.Wsh) + (long long)r * a.sWsh + g.wsh_off : nullptr;
+  T* WT = a.WTsh ? reinterpret_cast<T*>(a.WTsh) + (long long)r * a.sWTsh + g.wtsh_off : nullptr;
+#pragma unroll 4
+  for (int i = 0; i < 16; ++i) {
+    const int kk = (tid >> 6) + 4 * i, k = k0 + kk, n = n0 + nn;
+    float w = 0.f;
+    if (k < g.K && n < g.N) {
+      const long long pi = g.p_off + (long long)k * g.N + n;
+      w = opt_update(a.op, P[pi], grad(pi, sc_w), S, pi, iter);
+      P[pi] = w;
+      if (W) W[p0 * a.wsh_par + (long long)k * g.ldwsh + n] = from_f<T>(w);
+    }
+    tile[kk][nn] = w;
+  }
+  if (k0 == 0 && g.has_bias && tid < 64 && n0 + tid < g.N) {
+    const long long pi = g.p_off + (long long)g.K * g.N + n0 + tid;
+    P[pi] = opt_update(a.op, P[pi], grad(pi, sc_b), S, pi, iter);
+  }
+  if (!WT) return;
+  __syncthreads();
+#pragma unroll 4
+  for (int i = 0; i < 16; ++i) {
+    const int nl = (tid >> 6) + 4 * i, kl = tid & 63, k = k0 + kl, n = n0 + nl;
+    if (k < g.K && n < g.N) WT[p0 * a.wtsh_par + (long long)n * g.ldwtsh + k] = from_f<T>(tile[kl][nl]);
+  }
+}
+
+}  // namespace ea
+
+// the same update with the gradient clipped (clip.hip wrote cu->scale on this stream)
+extern "C" hipError_t ea_apply_update_clip(FlatArgs* a, int bf16, const ClipUpd* cu, hipStream_t s) {
+  const int tiles = shadow_tiles(*a);
+  a->total_blocks = a->R * tiles;
+  if (a->total_blocks <= 0) return hipSuccess;
+  if (bf16) hipLaunchKernelGGL((shadow_tiles_clip_kernel<__bf16>), dim3(a->total_blocks), dim3(256), 0, s, *a, tiles, *cu);
+  else hipLaunchKernelGGL((shadow_tiles_clip_kernel<float>), dim3(a->total_blocks), dim3(256), 0, s, *a, tiles, *cu);
+  return hipGetLastError();
+}

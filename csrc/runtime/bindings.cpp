@@ -28,6 +28,8 @@ extern "C" hipError_t ea_sum_slabs(const float* S, int ks, int M, int N, float* 
 extern "C" hipError_t ea_ps_sub(float* p, const float* d, long long n, float scale, int atomic, hipStream_t s);
 extern "C" hipError_t ea_poison_lds(unsigned pattern, hipStream_t s);
 extern "C" hipError_t ea_sub(const float* a, const float* b, float* out, long long n, hipStream_t s);
+extern "C" int ea_clip_layout(ea::ClipArgs* a);
+extern "C" hipError_t ea_clip_scales(const ea::ClipArgs* a, hipStream_t s);
 extern "C" hipError_t ea_shuffle_perm(int* perm, long long sPerm, const int* ntrain, int R, int nmax, uint32_t key,
                                       int shuffle, hipStream_t s);
 
@@ -139,6 +141,12 @@ static ExecCfg parse_cfg(const py::dict& d) {
   c.acc = get<uintptr_t>(d, "acc", 0);
   c.acc_stride = get<int>(d, "acc_stride", 6);
   c.ctr = get<uintptr_t>(d, "ctr", 0);
+  if (d.contains("clip") && !d["clip"].is_none()) {   // None = off
+    py::dict cl = d["clip"].cast<py::dict>();
+    c.clipvalue = get<float>(cl, "clipvalue", -1.f);
+    c.clipnorm = get<float>(cl, "clipnorm", -1.f);
+    c.global_clipnorm = get<float>(cl, "global_clipnorm", -1.f);
+  }
   return c;
 }
 
@@ -299,6 +307,41 @@ PYBIND11_MODULE(_C, m) {
         "replica_average");
   }, py::arg("P"), py::arg("sP"), py::arg("R"), py::arg("n"), py::arg("out"), py::arg("write_back"), py::arg("stream"),
      py::arg("scale") = 0.0);
+  // The gradient-clipping kernels (clip.hip: partial sums of squares, then scales) on the
+  // caller's buffers: G [R][sG] fp32, vars = [(offset, length)] of a row's variables; writes
+  // scale[r][t] = c / max(norm, c) into scales [R][CLIP_MAX_VAR] fp32 (per variable for
+  // clipnorm, one value for global_clipnorm; the norms of clamp(G * grad_scale)).  None = off.
+  m.attr("CLIP_MAX_VAR") = CLIP_MAX_VAR;
+  m.def("clip_scales", [](uintptr_t G, long long sG, int R, std::vector<std::pair<long long, long long>> vars,
+                          float grad_scale, py::object clipvalue, py::object clipnorm, py::object global_clipnorm,
+                          uintptr_t scales, uintptr_t s) {
+    ClipArgs a;
+    std::memset(&a, 0, sizeof(a));
+    if (vars.size() > (size_t)CLIP_MAX_VAR) throw std::invalid_argument("clip_scales: too many variables");
+    a.G = reinterpret_cast<const float*>(G);
+    a.sG = sG;
+    a.R = R;
+    a.nvar = (int)vars.size();
+    a.grad_scale = grad_scale;
+    a.clipvalue = clipvalue.is_none() ? -1.f : clipvalue.cast<float>();
+    a.clipnorm = clipnorm.is_none() ? -1.f : clipnorm.cast<float>();
+    a.global_clipnorm = global_clipnorm.is_none() ? -1.f : global_clipnorm.cast<float>();
+    for (int t = 0; t < a.nvar; ++t) {
+      a.var[t].off = vars[t].first;
+      a.var[t].len = vars[t].second;
+      if (vars[t].first < 0 || vars[t].second < 0 || vars[t].first + vars[t].second > sG)
+        throw std::invalid_argument("clip_scales: a variable lies outside the gradient row");
+    }
+    if (R <= 0 || !G || !scales || !ea_clip_layout(&a)) throw std::invalid_argument("clip_scales: bad arguments");
+    a.scale = reinterpret_cast<float*>(scales);
+    chk(hipMalloc(&a.part, sizeof(double) * (size_t)R * (size_t)(a.nchunk > 0 ? a.nchunk : 1)), "hipMalloc(clip partials)");
+    const hipError_t e = ea_clip_scales(&a, S(s));
+    const hipError_t e2 = hipStreamSynchronize(S(s));
+    (void)hipFree(a.part);
+    chk(e, "clip_scales");
+    chk(e2, "clip_scales");
+  }, py::arg("G"), py::arg("sG"), py::arg("R"), py::arg("vars"), py::arg("grad_scale"), py::arg("clipvalue"),
+     py::arg("clipnorm"), py::arg("global_clipnorm"), py::arg("scales"), py::arg("stream"));
   m.def("shuffle_perm", [](uintptr_t perm, long long sPerm, uintptr_t ntrain, int R, int nmax, uint32_t key,
                            int shuffle, uintptr_t s) {
     // per-replica keyed Feistel permutation of rows [0, ntrain[r]) (csrc/kernels/shuffle.hip)

@@ -17,6 +17,9 @@ extern "C" void ea_gemm_init();
 extern "C" hipError_t ea_gemm_table(const ea::TableArgs* ta, int bf16, int dw, hipStream_t s);
 extern "C" hipError_t ea_rowchain(const ea::RcArgs* a, int bf16, int nbw, hipStream_t s);
 extern "C" hipError_t ea_apply_update(ea::FlatArgs* a, int bf16, hipStream_t s);
+extern "C" hipError_t ea_apply_update_clip(ea::FlatArgs* a, int bf16, const ea::ClipUpd* cu, hipStream_t s);
+extern "C" int ea_clip_layout(ea::ClipArgs* a);
+extern "C" hipError_t ea_clip_scales(const ea::ClipArgs* a, hipStream_t s);
 extern "C" hipError_t ea_refresh_shadows(ea::FlatArgs* a, int bf16, hipStream_t s);
 extern "C" hipError_t ea_advance(long long* ctr, const int* ntrain, int R, int B, int n, hipStream_t s);
 extern "C" hipError_t ea_persist_post_average(unsigned* flags, int nflags, long long* ctr, const int* ntrain, int R,
@@ -53,6 +56,14 @@ Executor::Executor(const ExecCfg& cfg) : c_(cfg) {
   rc_.on = c_.rowchain != 0 && build_rowchain();
   if (c_.rowchain == 1 && !rc_) throw std::invalid_argument("row-chain plan requested but the model is not eligible");
   tl_.on = !rc_ && c_.rowchain != 0 && c_.tail != 0 && build_tail();
+  if (clipping()) {
+    // the persistent kernels update inside the launch, before the whole gradient exists
+    if (c_.clipnorm >= 0.f && c_.global_clipnorm >= 0.f)
+      throw std::invalid_argument("clipnorm and global_clipnorm cannot both be set");
+    if (c_.persist == 1) throw std::invalid_argument("persistent plan requested, but gradient clipping needs the materialised-gradient step");
+    build_clip();
+    return;
+  }
   // deep = 2 (tests, A/B): the layer pipeline even where persist.hip's roles are eligible
   dp_.on = c_.persist != 0 && c_.deep == 2 && build_deep();
   pm_.on = !dp_.on && c_.persist != 0 && build_persist();
@@ -74,6 +85,45 @@ Executor::~Executor() {
   if (d_dws_) (void)hipFree(d_dws_);
   if (d_dxg_) (void)hipFree(d_dxg_);
   if (d_dflags_) (void)hipFree(d_dflags_);
+  if (d_clip_part_) (void)hipFree(d_clip_part_);
+  if (d_clip_scale_) (void)hipFree(d_clip_scale_);
+}
+
+// Gradient clipping: variable 2l is layer l's kernel, 2l + 1 its bias (len 0 without one) --
+// the index the clipped update reads its scale at
+void Executor::build_clip() {
+  const int L = (int)c_.layers.size();
+  if (2 * L > CLIP_MAX_VAR) throw std::invalid_argument("too many layers for gradient clipping");
+  if (c_.G == 0) throw std::invalid_argument("gradient clipping needs the gradient buffer G");
+  std::memset(&clip_, 0, sizeof(clip_));
+  clip_.G = reinterpret_cast<const float*>(c_.G);
+  clip_.sG = c_.sG;
+  clip_.R = c_.R;
+  clip_.nvar = 2 * L;
+  clip_.grad_scale = c_.op.grad_scale;
+  clip_.clipvalue = c_.clipvalue;
+  clip_.clipnorm = c_.clipnorm;
+  clip_.global_clipnorm = c_.global_clipnorm;
+  for (int l = 0; l < L; ++l) {
+    const LayerCfg& ly = c_.layers[l];
+    const long long kn = (long long)ly.K * ly.N;
+    clip_.var[2 * l].off = ly.p_off;
+    clip_.var[2 * l].len = kn;
+    clip_.var[2 * l + 1].off = ly.p_off + kn;
+    clip_.var[2 * l + 1].len = ly.has_bias ? ly.N : 0;
+    if (ly.p_off < 0 || ly.p_off + kn + clip_.var[2 * l + 1].len > c_.nparams || c_.nparams > c_.sG)
+      throw std::invalid_argument("gradient clipping: a layer's parameters lie outside the gradient row");
+  }
+  if (!ea_clip_layout(&clip_)) throw std::invalid_argument("gradient clipping: bad variable table");
+  clip_.ctr = reinterpret_cast<const long long*>(c_.ctr);
+  clip_.ntrain = reinterpret_cast<const int*>(c_.ntrain);
+  clip_.B = c_.B;
+  if (c_.clipnorm >= 0.f || c_.global_clipnorm >= 0.f) {
+    check(hipMalloc(&d_clip_part_, sizeof(double) * (size_t)c_.R * (size_t)std::max(clip_.nchunk, 1)), "hipMalloc(clip partials)");
+    check(hipMalloc(&d_clip_scale_, sizeof(float) * (size_t)c_.R * CLIP_MAX_VAR), "hipMalloc(clip scales)");
+    clip_.part = d_clip_part_;
+    clip_.scale = d_clip_scale_;
+  }
 }
 
 // Persistent plan (persist.hip): 3 Dense layers, hidden widths 64 or 128, a last layer
@@ -547,6 +597,15 @@ void Executor::run_chunk(hipStream_t s, int nsteps) const {
     return;
   }
   for (int i = 0; i < nsteps; ++i) run_step(s, i);
+}
+
+// nsteps training steps of a clipping optimizer: every step through the materialised gradient.
+// apply() advances the counters by one, so each step runs at offset 0 and no advance follows.
+void Executor::run_clipped(hipStream_t s, int nsteps) {
+  for (int i = 0; i < nsteps; ++i) {
+    forward_backward(s);
+    apply(s);
+  }
 }
 
 // the post node of a persistent chunk: flag clear + counter advance, and (train_chunk_avg
@@ -1318,12 +1377,14 @@ std::vector<int> Executor::launch_cfgs() const {
 }
 
 void Executor::train_step(hipStream_t s) {
+  if (clipping()) return run_clipped(s, 1);
   run_chunk(s, 1);
   if (!persistent()) advance(1, s);   // the persistent chunk's post node advanced the counters
 }
 
 void Executor::train_chunk(int nsteps, hipStream_t s) {
   if (nsteps <= 0) return;
+  if (clipping()) return run_clipped(s, nsteps);
   run_chunk(s, nsteps);
   if (!persistent()) advance(nsteps, s);
 }
@@ -1417,7 +1478,15 @@ FlatArgs Executor::flat_args() const {
 
 void Executor::apply(hipStream_t s) {
   FlatArgs a = flat_args();
-  check(ea_apply_update(&a, c_.bf16, s), "apply_update");
+  if (clipping()) {
+    // partial sums of squares + scales (nothing for clipvalue alone), then the update on
+    // g = clamp(G * grad_scale) * scale
+    check(ea_clip_scales(&clip_, s), "clip_scales");
+    const ClipUpd cu{c_.clipvalue, d_clip_scale_};
+    check(ea_apply_update_clip(&a, c_.bf16, &cu, s), "apply_update(clip)");
+  } else {
+    check(ea_apply_update(&a, c_.bf16, s), "apply_update");
+  }
   advance(1, s);
 }
 
@@ -1459,8 +1528,12 @@ int Executor::capture(int nsteps, int mode, hipStream_t s) {
     if (mode == 0) {
       // one chunk: steps at offsets 0..nsteps-1 from the counter base, then one advance
       // (the persistent plan's post node includes it)
-      run_chunk(s, nsteps);
-      if (!persistent()) advance(nsteps, s);
+      if (clipping()) {
+        run_clipped(s, nsteps);
+      } else {
+        run_chunk(s, nsteps);
+        if (!persistent()) advance(nsteps, s);
+      }
     } else {
       for (int i = 0; i < nsteps; ++i) {
         if (mode == 1) forward_backward(s);

@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "../kernels/args.h"
+#include "../kernels/clip_args.h"
 
 namespace ea {
 
@@ -85,6 +86,11 @@ struct ExecCfg {
                         // 2 preferred over persist.hip (tests, A/B)
   int no_reorder = 0;   // A/B: keep a DW + DX launch's problems in declaration order
   int dual = 1;         // a layer's DW and DX on different tiles in one launch (0: two launches)
+  // optimizer gradient clipping (Keras clipvalue / clipnorm / global_clipnorm; < 0 = off).  Norm
+  // clipping needs the whole gradient before the first weight moves, so with any of them set
+  // every step runs as forward_backward -> G, [clip.hip partial sums, scales], clipped update
+  // (no persistent plan, no fused PK_DW_UPDATE epilogue)
+  float clipvalue = -1.f, clipnorm = -1.f, global_clipnorm = -1.f;
 };
 
 struct EvalSource {
@@ -114,7 +120,8 @@ class Executor {
   // counter advance; V1 / V2 roles and the layer pipeline)
   bool train_chunk_avg(int nsteps, hipStream_t s, float* out, int write_p, double scale, int mode = 1);
   void forward_backward(hipStream_t s);    // gradient path: writes G (no update)
-  void apply(hipStream_t s);               // gradient path: optimizer apply + advance
+  void apply(hipStream_t s);               // gradient path: [gradient clipping +] optimizer apply + advance
+  bool clipping() const { return c_.clipvalue >= 0.f || c_.clipnorm >= 0.f || c_.global_clipnorm >= 0.f; }
   void eval_chunk(long long chunk, const EvalSource& src, hipStream_t s);
   void refresh_shadows(bool both, hipStream_t s);
   // P[r] and both shadow parities of every replica rebuilt from src (a parameter-server
@@ -132,6 +139,10 @@ class Executor {
 
   // launches per step (a captured chunk adds one 1-block counter advance)
   int launches_per_step() const {
+    if (clipping()) {   // forward_backward, [partial sums, scales], clipped update, advance
+      const int fb = rc_.on ? 3 : (int)fwd_.size() + (int)bwd_.size();
+      return fb + (c_.clipnorm >= 0.f || c_.global_clipnorm >= 0.f ? 2 : 0) + 2;
+    }
     if (rc_.on) return 3;
     if (tl_.on) return (int)tl_.pre.size() + 1 + (int)tl_.post.size();
     return (int)fwd_.size() + (int)bwd_.size();
@@ -149,6 +160,7 @@ class Executor {
   // why this executor does not run a persistent plan ("" when it does, or was not asked to)
   std::string plan_reason() const {
     if (persistent() || c_.persist == 0) return "";
+    if (clipping()) return "gradient clipping needs the materialised-gradient step";
     return why_pm_ + (why_dp_.empty() ? "" : "; " + why_dp_);
   }
   // parameter-server hook of the persistent plan (V1 roles only): every step pushes the
@@ -241,6 +253,13 @@ class Executor {
   float* d_dxg_ = nullptr;         // its exchange buffer (per-step synchronous replicas)
   unsigned* d_dflags_ = nullptr;   // [R][2][DP_MAXWG] GO / phase counters
   bool build_deep();
+  // gradient clipping (clip.hip): the variable table, its partial sums [R][nchunk] and the
+  // scales [R][CLIP_MAX_VAR], allocated once here so apply() captures into a hipGraph
+  ClipArgs clip_{};
+  double* d_clip_part_ = nullptr;
+  float* d_clip_scale_ = nullptr;
+  void build_clip();
+  void run_clipped(hipStream_t s, int nsteps);   // nsteps x (forward_backward, apply)
   std::string why_pm_, why_dp_;   // why the persistent plans were not eligible (plan_reason)
   void run_chunk(hipStream_t s, int nsteps) const;   // nsteps training steps (no counter advance)
   void run_step(hipStream_t s, int step_off) const;

@@ -28,6 +28,7 @@ SOURCES = [
     "kernels/gemm_big_bf16.hip",
     "kernels/gemm_f32.hip",
     "kernels/flat.hip",
+    "kernels/clip.hip",
     "kernels/rowchain.hip",
     "kernels/persist.hip",
     "kernels/persist_local.hip",

@@ -23,6 +23,8 @@ import torch
 
 OPT_SGD, OPT_RMSPROP, OPT_ADAM, OPT_ADAGRAD, OPT_ADAMAX = 0, 1, 2, 3, 4
 
+_CLIP_KEYS = ("clipvalue", "clipnorm", "global_clipnorm")
+
 
 class Optimizer:
     _defaults: Dict[str, object] = {}
@@ -33,9 +35,17 @@ class Optimizer:
             kwargs["learning_rate"] = lr
         self._hyper = dict(self._defaults)
         decay = kwargs.pop("decay", 0.0)
-        for k in list(kwargs):
-            if k in ("clipnorm", "clipvalue", "global_clipnorm"):
-                self._hyper[k] = kwargs.pop(k)
+        for k in _CLIP_KEYS:
+            v = kwargs.pop(k, None)
+            if v is None:
+                continue
+            v = float(v)
+            if v < 0:
+                raise ValueError(f"Expected {k} >= 0, received: {v}")
+            self._hyper[k] = v
+        if "clipnorm" in self._hyper and "global_clipnorm" in self._hyper:
+            raise ValueError("Cannot accept both `clipnorm` and `global_clipnorm`, received: "
+                             f"clipnorm={self._hyper['clipnorm']}, global_clipnorm={self._hyper['global_clipnorm']}")
         unknown = set(kwargs) - set(self._defaults)
         if unknown:
             raise TypeError(f"Unexpected keyword argument(s) for {type(self).__name__}: {sorted(unknown)}")
@@ -83,10 +93,39 @@ class Optimizer:
         hyper = self.__dict__.get("_hyper", {})
         if item in hyper:
             return hyper[item]
+        if item in _CLIP_KEYS:   # unset: None, as in Keras
+            return None
         raise AttributeError(item)
 
     def decayed_lr(self, iteration: int) -> float:
         return self._hyper["learning_rate"] / (1.0 + self._hyper["decay"] * iteration)
+
+    # ---- gradient clipping (Keras 2.10 optimizer_v2: clipvalue, then clipnorm, then global_clipnorm)
+    def clip_args(self):
+        """(clipvalue, clipnorm, global_clipnorm) for the native engine, None = off (kept out of
+        the ``native()`` hyper-parameter dict, which is copied key by key into OptParams)."""
+        return tuple(self._hyper.get(k) for k in _CLIP_KEYS)
+
+    @torch.no_grad()
+    def clip_gradients(self, grads):
+        """The gradient list (one tensor per variable) the update rule sees: every element
+        clamped to [-clipvalue, clipvalue], then every variable scaled by
+        clipnorm / max(||g_t||, clipnorm), then the whole list by
+        global_clipnorm / max(sqrt(sum_t ||g_t||^2), global_clipnorm); fp32, norm = sqrt(sum(g*g)).
+        The list itself is returned when nothing is set."""
+        cv, cn, gn = self.clip_args()
+        if cv is None and cn is None and gn is None:
+            return grads
+        grads = [g.float() for g in grads]
+        if cv is not None:
+            grads = [torch.clamp(g, -cv, cv) for g in grads]
+        if cn is not None:
+            grads = [g * (cn / torch.clamp(torch.sqrt(torch.sum(g * g)), min=cn)) for g in grads]
+        if gn is not None and grads:
+            norm = torch.sqrt(torch.stack([torch.sum(g * g) for g in grads]).sum())
+            scale = gn / torch.clamp(norm, min=gn)
+            grads = [g * scale for g in grads]
+        return grads
 
     # ---- engines
     def native(self):

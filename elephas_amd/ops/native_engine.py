@@ -228,6 +228,11 @@ class NativeTrainer(TrainerBase):
         if nat is None:
             raise ValueError(f"optimizer {type(opt).__name__} is not supported by the native engine")
         self.opt_id, self.opt_hp, self.nstate = nat
+        # clipvalue / clipnorm / global_clipnorm: applied to the materialised gradient
+        # (csrc/kernels/clip.hip), so the executor builds no persistent plan with any of them set
+        cv, cn, gn = opt.clip_args()
+        self.clip = None if cv is None and cn is None and gn is None else dict(
+            clipvalue=cv, clipnorm=cn, global_clipnorm=gn)
         if self.loss.native is None:
             raise ValueError(f"loss {self.loss.name} is not supported by the native engine")
         if any(m.native is None for m in self.metrics) or len(self.metrics) > 4:
@@ -342,7 +347,8 @@ class NativeTrainer(TrainerBase):
             S=self.S.data_ptr(), sS=self.S.shape[1] * self.n,
             Wsh=self.Wsh.data_ptr(), sWsh=2 * self.Wsh.shape[2], wsh_par=self.Wsh.shape[2],
             WTsh=self.WTsh.data_ptr(), sWTsh=2 * self.WTsh.shape[2], wtsh_par=self.WTsh.shape[2],
-            opt=opt, loss=self.loss.native, metrics=[m.native for m in self.metrics],
+            opt=opt, clip=self.clip if ws is self.ws else None,
+            loss=self.loss.native, metrics=[m.native for m in self.metrics],
             acc=self.acc.data_ptr(), acc_stride=6, ctr=self.ctr.data_ptr())
 
     def _build_executor(self):
@@ -1234,6 +1240,8 @@ class NativeTrainer(TrainerBase):
             return 2 * ((nsteps + self.GRAPH_CHUNK - 1) // self.GRAPH_CHUNK)
         full, rest = divmod(nsteps, self.GRAPH_CHUNK)
         graphs = full + bin(rest).count("1")
+        if self.clip is not None:
+            return nsteps * self.exe.launches_per_step()   # a clipped step holds its own counter advance
         return nsteps * self.exe.launches_per_step() + graphs   # + one counter advance per graph
 
     @property
@@ -1264,6 +1272,10 @@ class NativeTrainer(TrainerBase):
             return (f"persistent V{var}{sy} (1 kernel + 1 post kernel per <= {self.GRAPH_CHUNK}-step chunk; per "
                     f"replica {nk0}x{nc0} layer-0 tiles of {kc0}x{cw} + {nch} row-chain workgroups{dw}; "
                     f"grid {grid})")
+        if self.clip is not None:
+            fb = "row-chain" if self.exe.rowchain() else "grouped"
+            return (f"{fb} gradient + clipping ({self.exe.launches_per_step()} launches per step: forward/backward "
+                    f"into G, clip norms and scales, clipped update, counter advance)")
         if self.exe.rowchain():
             return "row-chain (3 launches per step)"
         if self.exe.tailchain():

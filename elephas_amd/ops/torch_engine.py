@@ -187,7 +187,7 @@ class TorchTrainer(TrainerBase):
         grads = [g if g is not None else torch.zeros_like(p) for g, p in zip(grads, ps)]
         for p in ps:
             p.requires_grad_(False)
-        self.opts[r].apply_torch(ps, grads, self.state[r], self.iters[r])
+        self.opts[r].apply_torch(ps, self.opts[r].clip_gradients(grads), self.state[r], self.iters[r])
         self.iters[r] += 1
         return per.detach(), [m.detach() for m in mvals]
 
@@ -233,7 +233,9 @@ class TorchTrainer(TrainerBase):
                 allreduce(G)
                 for r in range(self.R):
                     if has[r]:
-                        grads = [g.reshape(sh) for g, sh in zip(torch.split(G[r], sizes), shapes)]
+                        # clipped after the aggregation: every replica clips the same mean gradient
+                        grads = self.opts[r].clip_gradients(
+                            [g.reshape(sh) for g, sh in zip(torch.split(G[r], sizes), shapes)])
                         self.opts[r].apply_torch(self.params[r], grads, self.state[r], self.iters[r])
                         self.iters[r] += 1
             for r in range(self.R):
